@@ -78,10 +78,14 @@ def _digest(path, extra=b""):
 def build(force=False, verbose=False):
     """Compile what is stale and link.  Safe under `torch.distributed.run`: an exclusive lock file serialises the ranks (the
     first one builds, the others find everything fresh), the library is linked to a temporary name and renamed into place,
-    and a link stamp (digest of all object digests) forces a relink when an earlier run died between compile and link."""
+    and a link stamp (digest of all object digests) forces a relink when an earlier run died between compile and link.
+    A fresh library is returned before the lock is taken: nothing is written, so a tree built by one user loads for another
+    who cannot write to it."""
+    if not force and not _plan(False)[3]:
+        return LIB
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    with open(os.path.join(OBJ, ".lock"), "w") as lock:
+    with _open_lock() as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
             return _build_locked(force, verbose)
@@ -89,8 +93,20 @@ def build(force=False, verbose=False):
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(force, verbose):
-    hipcc = _hipcc()
+def _open_lock():
+    """The lock file, opened for writing and made writable for every user when this process owns it: loaders of earlier
+    versions of this file open it on every import, fresh library or not, and the user who runs a tree need not be the one who
+    built it."""
+    fd = os.open(os.path.join(OBJ, ".lock"), os.O_WRONLY | os.O_CREAT, 0o666)
+    try:
+        os.fchmod(fd, 0o666)
+    except PermissionError:
+        pass
+    return os.fdopen(fd, "w")
+
+
+def _plan(force):
+    """(compile jobs, objects, link digest, relink needed).  Reads only."""
     jobs, objs, digs = [], [], []
     for src in _sources():
         sp = os.path.join(HERE, src)
@@ -104,6 +120,15 @@ def _build_locked(force, verbose):
         if not force and os.path.exists(op) and os.path.exists(stamp) and open(stamp).read() == dig:
             continue
         jobs.append((sp, op, stamp, dig))
+    link_dig = hashlib.sha1("\n".join(digs).encode()).hexdigest()
+    link_stamp = os.path.join(OBJ, "libafm_hip.so.sha1")
+    stale = bool(jobs) or not os.path.exists(LIB) or not os.path.exists(link_stamp) or open(link_stamp).read() != link_dig
+    return jobs, objs, link_dig, stale
+
+
+def _build_locked(force, verbose):
+    hipcc = _hipcc()
+    jobs, objs, link_dig, stale = _plan(force)
 
     def run(job):
         sp, op, stamp, dig = job
@@ -122,17 +147,14 @@ def _build_locked(force, verbose):
             for done in ex.map(run, jobs):
                 if verbose:
                     print("compiled", os.path.basename(done))
-    link_dig = hashlib.sha1("\n".join(digs).encode()).hexdigest()
-    link_stamp = os.path.join(OBJ, "libafm_hip.so.sha1")
-    stale = not os.path.exists(LIB) or not os.path.exists(link_stamp) or open(link_stamp).read() != link_dig
-    if jobs or stale:
+    if stale:
         tmp = LIB + f".tmp{os.getpid()}"
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
         os.replace(tmp, LIB)
-        with open(link_stamp, "w") as fh:
+        with open(os.path.join(OBJ, "libafm_hip.so.sha1"), "w") as fh:
             fh.write(link_dig)
     return LIB
 

@@ -79,3 +79,28 @@ def test_ops_refuse_cpu_tensors():
     a = torch.zeros(4, 8)
     with pytest.raises(AfmError):
         ops.gemm(a, a, torch.zeros(4, 4))   # the product path has no CPU fallback
+
+
+def test_fresh_library_loads_without_writing_to_the_tree(monkeypatch):
+    """A tree built by one user runs for another who cannot write to it: with the library fresh, build() and load() open
+    nothing for writing, create no directory and start no compiler."""
+    import builtins
+    import subprocess
+    from multimodalanalytical_amd import lib as L
+    from multimodalanalytical_amd.csrc import build as B
+    B.build()                                        # fresh from here on
+    real_open = builtins.open
+
+    def read_only_open(f, mode="r", *a, **k):
+        assert not set(mode) & set("wax+"), f"opened {f} with mode {mode}"
+        return real_open(f, mode, *a, **k)
+
+    def refuse(*a, **k):
+        raise AssertionError(f"wrote into the tree or started a compiler: {a}")
+    monkeypatch.setattr(builtins, "open", read_only_open)
+    monkeypatch.setattr(os, "open", refuse)
+    monkeypatch.setattr(os, "makedirs", refuse)
+    monkeypatch.setattr(subprocess, "run", refuse)
+    monkeypatch.setattr(L, "_lib", None)
+    assert B.build() == B.LIB
+    assert L.load().afm_abi_version() == L.ABI_VERSION

@@ -1,9 +1,8 @@
-"""CPU: the Hydra-style composer resolves this repo's configs/ tree and, when present (build
-container only), the REFERENCE's own configs/ tree with the reference test's override list
-(reference tests/test_run.py:8-18) to the same model / data / trainer settings."""
+"""CPU: the Hydra-style composer resolves this repo's configs/ tree to the same model / data / trainer settings as the
+REFERENCE's own configs/ tree with the reference test's override list (reference tests/test_run.py:8-18).  The reference
+tree's composition is stored in tests/golden/reference_configs.json (oracle/make_config_goldens.py)."""
+import json
 import os
-
-import pytest
 
 from multimodalanalytical_amd.config import compose, wrapper_kwargs
 
@@ -25,6 +24,14 @@ def _check(cfg):
     assert cfg["molecules"] is True and cfg["mixture"] is None
 
 
+def _reference(case, overrides):
+    """The reference tree's composition under `overrides`, as oracle/make_config_goldens.py stored it."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_configs.json")) as fh:
+        stored = json.load(fh)[case]
+    assert stored["overrides"] == overrides, "override list changed: regenerate tests/golden/reference_configs.json"
+    return stored["config"]
+
+
 def test_compose_own_tree():
     cfg = compose(os.path.join(ROOT, "configs"), "config_train", OVERRIDES)
     _check(cfg)
@@ -36,9 +43,8 @@ def test_compose_own_tree():
     assert cfg["model"]["d_model"] == 768 and cfg["model"]["lr"] == 1e-3 and cfg["model"]["gated_linear"] is True
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="reference tree only exists in the build container")
 def test_compose_reference_tree_unchanged():
-    cfg = compose("/root/reference/configs", "config_train", OVERRIDES)
+    cfg = _reference("test_run_overrides", OVERRIDES)
     _check(cfg)
     ours = compose(os.path.join(ROOT, "configs"), "config_train", OVERRIDES)
     assert ours["model"] == cfg["model"]
@@ -86,8 +92,7 @@ def test_compose_mixture_run_groups():
     assert plan["target_modality"] == "Smiles" and plan["model_config"]["align_config"]["output_dimension"] == 1800
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="reference tree only exists in the build container")
 def test_mixture_run_groups_equal_the_reference_tree():
     ours = compose(os.path.join(ROOT, "configs"), "config_train", C5)
-    ref = compose("/root/reference/configs", "config_train", C5)
+    ref = _reference("mixture_run_groups", C5)
     assert ours["data"] == ref["data"] and ours["mixture"] == ref["mixture"] and ours["model"] == ref["model"]
