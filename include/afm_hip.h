@@ -47,7 +47,10 @@ extern "C" {
  *   6  padded rows in the FORWARD pass of a training step: afm_gemm_desc.reserved2 bit 1 (k_live in the forward sense), afm_ln_shape.row_live
  *      read by afm_layernorm_fwd, afm_ln_shape.row_map (compaction of the live positions at the embedder), afm_attn_fwd honours
  *      reserved bit 6, afm_attn_shape.q_off / k_off (packed rows); exports added: afm_compact_plan, afm_permute_rows.  The ablation selector of AFM_ATTN_ABLATIONS builds moved to
- *      afm_attn_shape.reserved bits 20-27 (it overlapped the live selectors 16384 / 32768 / 65536). */
+ *      afm_attn_shape.reserved bits 20-27 (it overlapped the live selectors 16384 / 32768 / 65536).
+ *      Additive under 6 (no struct changed): the deterministic-mode exports (afm_gemm_group_det, afm_colsum_det, afm_scatter_add_rows_det,
+ *      afm_ce_fwd_det, afm_masked_mean_fwd_det, afm_align_loss_det and their *_ws_floats size queries), afm_ln_shape.flags bit 1, and
+ *      afm_gemm_desc.reserved2 bit 4. */
 #define AFM_ABI_VERSION 6
 
 enum { AFM_OK = 0, AFM_ERR_ARG = -1, AFM_ERR_UNSUPPORTED = -2, AFM_ERR_LAUNCH = -3 };
@@ -144,7 +147,10 @@ typedef struct {
                              bit 3 (8), with bit 1: the dead tiles of C (and of a stored pre_act) are NOT written -- the caller vouches that its
                              buffers already hold finite values there (persistent buffers only these kernels ever write: stale rows of an earlier
                              step), so the zero fill -- HBM writes for rows nobody reads -- is left out.  Without bit 1 (the backward's hint): the same for the
-                             zero tiles of the data-gradient forms, on the caller's word (afm_last_hint) that every consumer of C takes the hint too. */
+                             zero tiles of the data-gradient forms, on the caller's word (afm_last_hint) that every consumer of C takes the hint too.
+                             bit 4 (16): the caller asks for the deterministic result (see "Deterministic mode"): the other forms never split K
+                             over workgroups then (no atomics); the wgrad form (transA, !transB) needs afm_gemm_group_det's workspace, so afm_gemm
+                             and afm_gemm_group refuse it with AFM_ERR_UNSUPPORTED; afm_gemm_group_det takes the descriptor either way. */
   const uint8_t* k_live;  /* nullable: k_live[i] == 0 says the STORED rows 64 i .. 64 i + 63 of A (64 token positions) are all zero --
                              the padded positions of a training step's backward, whose activation gradients are exact zeros.
                              wgrad form (transA): the MFMA kernels leave those k-steps out (K / 64 bytes).  NT form without bias /
@@ -218,7 +224,10 @@ typedef struct {
                              mean / rstd get zeros there.  A hint: the scalar kernels (d % 8 != 0, rows < 64) ignore it. */
   int32_t flags;           /* bit 0, with row_live: the rows row_live calls dead are NOT written (no zeros).  Forward: the caller's y / x_sum / mean /
                              rstd already hold finite values there (a persistent buffer only these kernels ever write).  Backward: the caller has
-                             checked (afm_last_hint) that every consumer of dx / dx_drop takes the hint too, so nothing loads those rows. */
+                             checked (afm_last_hint) that every consumer of dx / dx_drop takes the hint too, so nothing loads those rows.
+                             bit 1 (2), backward: deterministic mode -- dgamma / dbeta are added WITHOUT atomics: block partials to `partial`
+                             (afm_layernorm_bwd_ws_floats of the same shape, flags included: > 0 for every shape), then a fixed-order reduce;
+                             the block count is a function of (rows, d) alone.  `partial` must then be given (AFM_ERR_ARG otherwise). */
   int32_t reserved;
   const int32_t* row_map;  /* nullable, placement form (seg_len != 0) only, forward and backward: position p = out_off + r % seg_len of sample
                              b = r / seg_len lives in row row_map[b * out_seg_stride + p] of the concatenated-sequence matrix instead of row
@@ -554,6 +563,53 @@ int afm_scaler_update(float* scaler, const float* sumsq, float growth, float bac
  * when it cannot be found.  Bootstrap: rank 0 calls afm_comm_unique_id, the 128 bytes travel to the other ranks by any means
  * (the host side uses its torch.distributed store), every rank calls afm_comm_create with the current device selected.
  * ---------------------------------------------------------------------------------------- */
+/* ------------------------------------------------------------------------------------------
+ * Deterministic mode.  The default kernels finish every reduction over tokens with fp32 atomics, whose order changes from run to
+ * run.  These forms give the same bits in every run and on every MI355X for the same inputs: each first launch stores its partial
+ * sums to a caller-provided workspace (`ws`, `ws_floats` floats, 16-byte aligned), a second launch adds them in a fixed order.  The
+ * plan (kernel, split count, block count, summation order) is a function of the shapes, dtypes and operand alignment only -- no
+ * occupancy query, device attribute or environment variable takes part.  A call whose workspace is missing or too small returns
+ * AFM_ERR_ARG, a problem outside the form AFM_ERR_UNSUPPORTED; nothing is launched then, and nothing falls back to atomics.
+ * The *_ws_floats queries are host-only (no device is touched) and return -1 for an invalid shape.  afm_gemm_group_det_ws_floats takes
+ * the descriptors with the pointers of the call: operand alignment decides which kernel a problem takes, so it enters the plan and the
+ * size (null pointers count as aligned); a call whose workspace is then too small is refused with AFM_ERR_ARG.
+ * (afm_layernorm_bwd: afm_ln_shape.flags bit 1.  The rest of a training step -- forward GEMMs, attention, dropout, the clip norm,
+ * Adam -- has no atomics.)
+ *
+ * afm_gemm_group_det: weight-gradient problems only (transA, !transB, fp32 C, no bias / residual / pre_act / activation / dropout;
+ *   accumulate, a_colsum, glu_rows, k_live and reserved2 bits 2-4 as in afm_gemm).  Problem i is split into a fixed number of
+ *   k-chunks (<= 16 on the MFMA kernel, <= 64 on the fp32 one); chunk s stores its fp32 partial of C to slab s and its partial column sums of A next to it; the slabs are then
+ *   added to C (to 0 without accumulate) and a_colsum in chunk order.  16-bit operands of the grouped-wgrad shapes (see
+ *   afm_gemm_group) run the grouped MFMA kernel, everything else an fp32 FMA kernel (fp32, split pairs -- hi + lo exactly --, small
+ *   shapes).  count = 1 covers a single GEMM.  The problems must not alias each other's C.
+ * afm_colsum_det: afm_colsum with row chunks of >= 256 rows (at most 256 chunks) summed in order.
+ * afm_scatter_add_rows_det: afm_scatter_add_rows with `order` = the row indices 0 .. n-1 sorted STABLY by the key
+ *   (id == padding_idx ? V : id clamped to [0, V)) (e.g. a stable device sort), and seg_end[i] = one past the last sorted position of
+ *   the key that starts at sorted position i (read at the positions where the key changes): dtable[v, c] gets, for the rows r0 < r1 < ... whose id
+ *   maps to v (padding rows skipped), the sequential fp32 sum
+ *   ((dtable[v, c] + dout[r0, c] * s(r0)) + dout[r1, c] * s(r1)) + ...  with every product and sum rounded on its own (no fused
+ *   multiply-add): bit-exact against a CPU emulation of that order.
+ * afm_ce_fwd_det / afm_align_loss_det / afm_masked_mean_fwd_det: the block sums of the loss (stats) / of the pooled chunks go to
+ *   `ws` and are added in block order.
+ * Multi-GPU: the gradient all-reduce (afm_allreduce_bucket) sums in the order RCCL chooses; deterministic mode covers one rank.
+ * ---------------------------------------------------------------------------------------- */
+int64_t afm_gemm_group_det_ws_floats(const afm_gemm_desc* descs, int32_t count);
+int afm_gemm_group_det(const afm_gemm_desc* descs, int32_t count, float* ws, int64_t ws_floats, void* stream);
+int64_t afm_colsum_det_ws_floats(int64_t rows, int32_t n);
+int afm_colsum_det(const void* x, float* out, int64_t rows, int32_t n, int32_t ld, int32_t dtype, int32_t accumulate,
+                   float* ws, int64_t ws_floats, void* stream);
+int afm_scatter_add_rows_det(const int64_t* ids, const int64_t* order, const int64_t* seg_end, const float* scale, const float* dout,
+                             float* dtable, int64_t n, int32_t d, int32_t V, int64_t padding_idx, void* stream);
+int64_t afm_ce_fwd_det_ws_floats(int64_t rows);
+int afm_ce_fwd_det(const float* logits, const int64_t* labels, int64_t rows, int32_t V, int32_t ld, float* row_lse,
+                   int64_t* argmax, float* stats, float* ws, int64_t ws_floats, void* stream);
+int64_t afm_masked_mean_fwd_det_ws_floats(int32_t B, int32_t S, int32_t d);
+int afm_masked_mean_fwd_det(const void* x, int32_t x_dtype, const uint8_t* key_pad, int32_t B, int32_t S, int32_t d, float* out,
+                            float* ws, int64_t ws_floats, void* stream);
+int64_t afm_align_loss_det_ws_floats(int32_t B, int32_t n);
+int afm_align_loss_det(const float* z, const float* target, int32_t kind, int32_t B, int32_t n, float grad_scale,
+                       const float* scale_dev, float* stats, float* dz, float* ws, int64_t ws_floats, void* stream);
+
 typedef struct afm_comm afm_comm;
 int afm_comm_unique_id(void* out128);
 int afm_comm_create(afm_comm** out, const void* id128, int32_t rank, int32_t world);

@@ -81,7 +81,9 @@ def build_plan(cfg: Dict[str, Any], shard_meta: Dict[str, Dict[str, Any]], n_tra
             "n_beams": model_cfg.get("n_beams", 10), "monitor": tr["checkpoint_monitor"],
             "monitor_mode": "min" if "loss" in tr["checkpoint_monitor"] else "max",          # trainer/trainer.py:34
             "acc_batches": tr["acc_batches"], "clip_grad": tr["clip_grad"], "epochs": tr["epochs"],
-            "limit_val_batches": tr.get("limit_val_batches", 1.0), "early_stopping_patience": tr.get("early_stopping_patience")}
+            "limit_val_batches": tr.get("limit_val_batches", 1.0), "early_stopping_patience": tr.get("early_stopping_patience"),
+            # +trainer.deterministic=true (Lightning's Trainer(deterministic=True)): the engine's deterministic mode; None = AFM_DETERMINISTIC
+            "deterministic": None if tr.get("deterministic") is None else bool(tr["deterministic"])}
 
 
 # ------------------------------------------------------------------------------------------------ shards
@@ -332,7 +334,7 @@ def run(cfg: Dict[str, Any], own: Dict[str, str]) -> Dict[str, Any]:
     def new_model():
         return HFWrapper(dc, target_tokenizer=tok, num_steps=plan["train_steps"], modality_dropout=plan["modality_dropout"],
                          multimodal_norm=plan["model_config"].get("multimodal_norm", True), clip_grad=plan["clip_grad"],
-                         world_size=world, device=device, compute_dtype=cd, backward_dtype=bd, **mk)
+                         world_size=world, device=device, compute_dtype=cd, backward_dtype=bd, deterministic=plan["deterministic"], **mk)
     model = new_model()
     loop = TrainLoop(model, acc_batches=plan["acc_batches"], world_size=world)
     if mk.get("model_checkpoint_path"):

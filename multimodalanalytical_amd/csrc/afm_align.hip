@@ -2,10 +2,12 @@
 // encoder output, its backward, and the sigmoid + mse / mae / sid loss with its gradient.  HBM-bound:
 // the pooling reads B*S*d activations once (split over S with fp32 atomics so the chip is filled).
 #include "afm_common.h"
+#include "afm_det.h"
 
 
-// grid (d / 256, B, SPLIT): partial sums over an S-chunk, divided by the row's kept-token count
-template <typename T>
+// grid (d / 256, B, SPLIT): partial sums over an S-chunk, divided by the row's kept-token count.  DET (afm_masked_mean_fwd_det): `out`
+// is the workspace, chunk z stores to out[(z * B + b) * d + c]; DET = false is the default kernel, unchanged.
+template <typename T, bool DET = false>
 __global__ __launch_bounds__(256) void k_masked_mean_fwd(const T* __restrict__ x, const uint8_t* __restrict__ key_pad,
                                                          int S, int d, float* __restrict__ out) {
   const int c = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
@@ -24,7 +26,8 @@ __global__ __launch_bounds__(256) void k_masked_mean_fwd(const T* __restrict__ x
   float acc = 0.f;
   for (int s = s0; s < s1; ++s)
     if (kp[s] == 0) acc += ld_rc(x, (int64_t)b * S + s, c, d * RowMul<T>::v);
-  atomicAdd(out + (int64_t)b * d + c, acc * inv);
+  if constexpr (DET) out[((int64_t)blockIdx.z * gridDim.y + b) * d + c] = acc * inv;
+  else atomicAdd(out + (int64_t)b * d + c, acc * inv);
 }
 
 __global__ __launch_bounds__(256) void k_masked_mean_bwd(const float* __restrict__ dy, const uint8_t* __restrict__ key_pad,
@@ -51,6 +54,8 @@ __global__ __launch_bounds__(256) void k_masked_mean_bwd(const float* __restrict
   }
 }
 
+// DET (afm_align_loss_det): `stats` is the workspace, block b stores its loss sum to stats[b]
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_align_loss(const float* __restrict__ z, const float* __restrict__ target, int kind,
                                                     int B, int64_t total, float grad_scale, const float* __restrict__ scale_dev, float* __restrict__ stats,
                                                     float* __restrict__ dz) {
@@ -74,7 +79,16 @@ __global__ __launch_bounds__(256) void k_align_loss(const float* __restrict__ z,
   __shared__ float part[4];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(stats, part[0] + part[1] + part[2] + part[3]);
+  if constexpr (DET) { if (threadIdx.x == 0) stats[blockIdx.x] = part[0] + part[1] + part[2] + part[3]; }
+  else if (threadIdx.x == 0) atomicAdd(stats, part[0] + part[1] + part[2] + part[3]);
+}
+
+// S-chunks of the pooling (fp32 atomics by default, a workspace slab each in the deterministic form)
+static int masked_mean_split(int32_t B, int32_t S, int32_t d) {
+  int split = 2048 / (((d + 255) / 256) * B);
+  if (split < 1) split = 1;
+  if (split > (S + 31) / 32) split = (S + 31) / 32;
+  return split < 1 ? 1 : split;
 }
 
 extern "C" int afm_masked_mean_fwd(const void* x, int32_t x_dtype, const uint8_t* key_pad, int32_t B, int32_t S,
@@ -82,12 +96,25 @@ extern "C" int afm_masked_mean_fwd(const void* x, int32_t x_dtype, const uint8_t
   if (!x || !key_pad || !out || B <= 0 || S <= 0 || d <= 0) return AFM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * d, st) != hipSuccess) return AFM_ERR_LAUNCH;
-  int split = 2048 / (((d + 255) / 256) * B);
-  if (split < 1) split = 1;
-  if (split > (S + 31) / 32) split = (S + 31) / 32;
-  const dim3 grid((d + 255) / 256, B, split);
+  const dim3 grid((d + 255) / 256, B, masked_mean_split(B, S, d));
   AFM_DT_SWITCH(x_dtype, T, AFM_LAUNCH(k_masked_mean_fwd<T>, grid, dim3(256), 0, st, (const T*)x, key_pad, S, d, out));
   return AFM_OK;
+}
+
+// Deterministic form: each S-chunk's share goes to `ws` (split x B x d), a reduce adds the chunks in order into out.
+extern "C" int64_t afm_masked_mean_fwd_det_ws_floats(int32_t B, int32_t S, int32_t d) {
+  if (B <= 0 || S <= 0 || d <= 0) return -1;
+  return (int64_t)masked_mean_split(B, S, d) * B * d;
+}
+extern "C" int afm_masked_mean_fwd_det(const void* x, int32_t x_dtype, const uint8_t* key_pad, int32_t B, int32_t S, int32_t d, float* out,
+                                       float* ws, int64_t ws_floats, void* stream) {
+  if (!x || !key_pad || !out || B <= 0 || S <= 0 || d <= 0) return AFM_ERR_ARG;
+  if (!ws || ws_floats < afm_masked_mean_fwd_det_ws_floats(B, S, d)) return AFM_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int split = masked_mean_split(B, S, d);
+  const dim3 grid((d + 255) / 256, B, split);
+  AFM_DT_SWITCH(x_dtype, T, AFM_LAUNCH((k_masked_mean_fwd<T, true>), grid, dim3(256), 0, st, (const T*)x, key_pad, S, d, ws));
+  return afm_det_sum_launch(ws, split, (int64_t)B * d, B, d, d, out, d, 0, st);
 }
 
 extern "C" int afm_masked_mean_bwd(const float* dy, const uint8_t* key_pad, int32_t B, int32_t S, int32_t d,
@@ -106,6 +133,22 @@ extern "C" int afm_align_loss(const float* z, const float* target, int32_t kind,
   const int64_t total = (int64_t)B * n;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  AFM_LAUNCH(k_align_loss, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z, target, kind, B, total, grad_scale, scale_dev, stats, dz);
+  AFM_LAUNCH(k_align_loss<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z, target, kind, B, total, grad_scale, scale_dev, stats, dz);
   return AFM_OK;
+}
+
+// Deterministic form: per-block loss sums to `ws`, one workgroup adds them in a fixed order into stats[0].
+extern "C" int64_t afm_align_loss_det_ws_floats(int32_t B, int32_t n) {
+  if (B <= 0 || n <= 0) return -1;
+  const int64_t blocks = ((int64_t)B * n + 255) / 256;
+  return blocks > 1024 ? 1024 : blocks;
+}
+extern "C" int afm_align_loss_det(const float* z, const float* target, int32_t kind, int32_t B, int32_t n, float grad_scale,
+                                  const float* scale_dev, float* stats, float* dz, float* ws, int64_t ws_floats, void* stream) {
+  if (!z || !target || !stats || B <= 0 || n <= 0 || kind < 0 || kind > 2) return AFM_ERR_ARG;
+  const int64_t blocks = afm_align_loss_det_ws_floats(B, n);
+  if (!ws || ws_floats < blocks) return AFM_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  AFM_LAUNCH(k_align_loss<true>, dim3((unsigned)blocks), dim3(256), 0, st, z, target, kind, B, (int64_t)B * n, grad_scale, scale_dev, ws, dz);
+  return afm_det_total_launch(ws, (int)blocks, 1, stats, st);
 }

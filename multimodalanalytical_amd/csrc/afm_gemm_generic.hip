@@ -262,7 +262,7 @@ static int gemm_generic(const afm_gemm_desc* d, hipStream_t st) {
   const int gx = (d->N + GT - 1) / GT, gy = (d->M + GT - 1) / GT;
   int splits = 1;
   const bool can_split = d->c_dtype == AFM_F32 && d->act == AFM_ACT_NONE && !d->pre_act && d->drop.p <= 0.f;
-  if (can_split && (int64_t)gx * gy < 256 && d->K >= 2048) {
+  if (can_split && !(d->reserved2 & 16) && (int64_t)gx * gy < 256 && d->K >= 2048) {   // (reserved2 bit 4: no split, no atomics)
     splits = (int)((512 + (int64_t)gx * gy - 1) / ((int64_t)gx * gy));
     const int maxs = d->K / 512;
     if (splits > maxs) splits = maxs;
@@ -311,6 +311,8 @@ extern "C" int afm_gemm(const afm_gemm_desc* d, void* stream) {
     if ((ca == 2 && (d->lda & 1)) || (cb == 2 && (d->ldb & 1))) return AFM_ERR_ARG;
   }
   if (d->a_colsum && !d->transA) return AFM_ERR_ARG;
+  // deterministic result asked for: the wgrad form needs afm_gemm_group_det (a workspace); the other forms never split K then
+  if ((d->reserved2 & 16) && d->transA && !d->transB) return AFM_ERR_UNSUPPORTED;
   afm_note_hint(d->k_live ? -1 : 0);      // (a kernel that takes the hint notes 1)
   if (d->M == 0 || d->N == 0) return AFM_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -331,6 +333,8 @@ extern "C" int afm_gemm(const afm_gemm_desc* d, void* stream) {
 extern "C" int afm_gemm_group(const afm_gemm_desc* descs, int32_t count, void* stream) {
   if (count < 0 || (count > 0 && !descs)) return AFM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
+  for (int i = 0; i < count; ++i)      // deterministic wgrad asked for: afm_gemm_group_det
+    if ((descs[i].reserved2 & 16) && descs[i].transA && !descs[i].transB) return AFM_ERR_UNSUPPORTED;
   const afm_gemm_desc* grp[2][8];
   int ng[2] = {0, 0};
   int hint = 0;      // over all problems: -1 if any given hint was ignored, else 1 if any was honoured (afm_last_hint)

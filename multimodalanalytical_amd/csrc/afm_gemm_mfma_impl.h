@@ -1441,6 +1441,10 @@ struct TnProb {
   int unit0;       // grouped launch: index of this problem's first (tile, k-chunk) unit
   int deal;        // afm_gemm_desc.reserved2 bit 2 (with k_live): k-steps dealt round-robin to the problem's units instead of contiguous chunks
 };
+// SLAB (deterministic mode, afm_gemm_group_det): no atomics.  The unit of k-chunk ks_id STORES its fp32 partial tile to slab ks_id
+// of C (g.C + ks_id * M * ldc) and each wave's partial column sums to a_colsum[((ks_id * tiles_n + n-tile) * 4 + wn) * M + m]; a
+// reduce launch adds the slabs in index order.  SLAB = false is the default kernel, unchanged.
+template <bool SLAB = false>
 __device__ __forceinline__ void tn256_unit(const TnProb& g, int tile, int ks_id, unsigned char* lds) {
   constexpr int S = 2, TBM = 256, TBN = 256, NW = 8, NIW = 8;
   constexpr int ABYTES = 64 * TBM * 2, STAGE = 64 * (TBM + TBN) * 2;
@@ -1586,10 +1590,14 @@ __device__ __forceinline__ void tn256_unit(const TnProb& g, int tile, int ks_id,
       s += __shfl_xor(s, 16, 64);
       s += __shfl_xor(s, 32, 64);
       const int mm = m0 + wm * 128 + i * 16 + fr;
-      if (fq == 0 && mm < g.M) atomicAdd(g.a_colsum + (g.glu_f ? glu_deint(mm, g.glu_f) : mm), s);
+      if (fq == 0 && mm < g.M) {
+        float* cs_dst = g.a_colsum + (g.glu_f ? glu_deint(mm, g.glu_f) : mm);
+        if constexpr (SLAB) cs_dst[(int64_t)((ks_id * g.tiles_n + tile % g.tiles_n) * 4 + wn) * g.M] = s;
+        else atomicAdd(cs_dst, s);
+      }
     }
   }
-  float* C = g.C;
+  float* C = SLAB ? g.C + (int64_t)ks_id * g.M * g.ldc : g.C;
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -1600,7 +1608,8 @@ __device__ __forceinline__ void tn256_unit(const TnProb& g, int tile, int ks_id,
         const int mm = m0 + wm * 128 + i * 16 + fq * 4 + r;
         if (mm < g.M && n < g.N) {
           float* c = C + (int64_t)(g.glu_f ? glu_deint(mm, g.glu_f) : mm) * g.ldc + n;
-          if (g.ksplit > 1) atomicAdd(c, acc[i][j][r]);
+          if constexpr (SLAB) *c = acc[i][j][r];
+          else if (g.ksplit > 1) atomicAdd(c, acc[i][j][r]);
           else *c = acc[i][j][r] + (g.accumulate ? *c : 0.f);
         }
       }
@@ -1626,6 +1635,7 @@ __global__ __launch_bounds__(512) void k_gemm_tn_ring256(MfmaArgs g) {
 #define AFM_TN_GROUP_MAX 8
 #define TN_LIST_MAX_BYTES (4 * (TN_LIST_MAX + 1))
 struct TnGroup { int n, units; TnProb p[AFM_TN_GROUP_MAX]; };
+template <bool SLAB = false>
 __global__ __launch_bounds__(512) void k_gemm_tn_group256(TnGroup gr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int bid = xcd_remap(blockIdx.x, gr.units);
@@ -1635,7 +1645,7 @@ __global__ __launch_bounds__(512) void k_gemm_tn_group256(TnGroup gr) {
     if (i < gr.n && bid >= gr.p[i].unit0) pi = i;
   const TnProb pr = gr.p[pi];
   const int local = bid - pr.unit0;
-  tn256_unit(pr, local % pr.ntile, local / pr.ntile, lds);
+  tn256_unit<SLAB>(pr, local % pr.ntile, local / pr.ntile, lds);
 }
 
 #include "afm_gemm_tnw4_impl.h"
@@ -2076,7 +2086,7 @@ int AFM_E16_FN(afm_gemm_tn_group_launch)(const afm_gemm_desc* const* ds, int cou
   for (int i = count; i < AFM_TN_GROUP_MAX; ++i) { gr.p[i] = gr.p[0]; gr.p[i].unit0 = 0x7fffffff; }
   static AfmOncePerDevice attr;
   if (attr.need()) {
-    (void)hipFuncSetAttribute((const void*)k_gemm_tn_group256, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 512 * 2 + TN_LIST_MAX_BYTES);
+    (void)hipFuncSetAttribute((const void*)k_gemm_tn_group256<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 512 * 2 + TN_LIST_MAX_BYTES);
     (void)hipFuncSetAttribute((const void*)k_gemm_tn_groupw4, hipFuncAttributeMaxDynamicSharedMemorySize, TW4_RING + TN_LIST_MAX_BYTES);
   }
   // every problem made of whole 256 x 256 tiles (all of a layer stack's weight gradients): the four-wave unit; a descriptor with
@@ -2094,7 +2104,41 @@ int AFM_E16_FN(afm_gemm_tn_group_launch)(const afm_gemm_desc* const* ds, int cou
     afm_set_last_algo("mfma_tn_groupw4");
     return AFM_OK;
   }
-  AFM_LAUNCH(k_gemm_tn_group256, dim3(units), dim3(512), 2 * 64 * 512 * 2 + TN_LIST_MAX_BYTES, st, gr);
+  AFM_LAUNCH(k_gemm_tn_group256<false>, dim3(units), dim3(512), 2 * 64 * 512 * 2 + TN_LIST_MAX_BYTES, st, gr);
   afm_set_last_algo("mfma_tn_group256");
+  return AFM_OK;
+}
+
+// Deterministic form (afm_gemm_group_det): count <= AFM_TN_GROUP_MAX eligible problems, problem i split into ksplit[i] k-chunks as
+// the host plan says (a function of the shapes only), each unit storing its partial tile to slab[i] + ks * M * N and its partial
+// column sums to cs_slab[i] (ksplit * tiles_n * 4 rows of M, see tn256_unit); nothing is added to C or a_colsum here.
+int AFM_E16_FN(afm_gemm_tn_group_det_launch)(const afm_gemm_desc* const* ds, const int* ksplit, float* const* slab, float* const* cs_slab,
+                                             int count, hipStream_t st) {
+  if (count < 1 || count > AFM_TN_GROUP_MAX) return AFM_ERR_ARG;
+  TnGroup gr;
+  gr.n = count;
+  int units = 0, st_ = 0;
+  for (int i = 0; i < count; ++i) {
+    const afm_gemm_desc* d = ds[i];
+    TnProb& pr = gr.p[i];
+    const int steps = d->K / 64, per = (steps + ksplit[i] - 1) / ksplit[i];
+    if (ksplit[i] < 1 || (steps + per - 1) / per != ksplit[i]) return AFM_ERR_ARG;
+    pr.A = (const e16*)d->A; pr.B = (const e16*)d->B; pr.C = slab[i]; pr.a_colsum = d->a_colsum ? cs_slab[i] : nullptr;
+    pr.k_live = d->k_live; pr.deal = (d->reserved2 & 4) != 0;
+    pr.M = d->M; pr.N = d->N; pr.K = d->K; pr.lda = d->lda; pr.ldb = d->ldb; pr.ldc = d->N;
+    pr.tiles_n = (d->N + 255) / 256; pr.ntile = ((d->M + 255) / 256) * pr.tiles_n;
+    pr.glu_f = d->glu_rows; pr.accumulate = 1;
+    pr.ksplit = ksplit[i]; pr.kchunk = per * 64; pr.unit0 = units;
+    units += pr.ntile * pr.ksplit;
+    if (d->k_live) st_ = (per <= TN_LIST_MAX && st_ >= 0) ? 1 : -1;
+  }
+  afm_note_hint(st_);
+  gr.units = units;
+  for (int i = count; i < AFM_TN_GROUP_MAX; ++i) { gr.p[i] = gr.p[0]; gr.p[i].unit0 = 0x7fffffff; }
+  static AfmOncePerDevice attr;
+  if (attr.need())
+    (void)hipFuncSetAttribute((const void*)k_gemm_tn_group256<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 512 * 2 + TN_LIST_MAX_BYTES);
+  AFM_LAUNCH(k_gemm_tn_group256<true>, dim3(units), dim3(512), 2 * 64 * 512 * 2 + TN_LIST_MAX_BYTES, st, gr);
+  afm_set_last_algo("mfma_tn_group256_det");
   return AFM_OK;
 }

@@ -6,6 +6,7 @@
 // reduce kernel (row-per-wave scalar kernels).
 #include <algorithm>
 #include "afm_common.h"
+#include "afm_det.h"
 
 #define LN_MAXV 32  // up to d = 2048 held in registers (template NV = ceil(d/64) rounded up)
 
@@ -250,7 +251,9 @@ __global__ __launch_bounds__(256) void k_ln_fwd_vec(const float* x, const float*
   }
 }
 
-template <typename TY, int NC>
+// DET (afm_ln_shape.flags bit 1, deterministic mode): `dgamma` is the workspace, the block sums are stored to dgamma[block][2d]
+// instead of added with atomics; DET = false is the default kernel, unchanged.
+template <typename TY, int NC, bool DET = false>
 __global__ __launch_bounds__(256) void k_ln_bwd_vec(const TY* __restrict__ dy, const float* __restrict__ x,
                                                     const float* __restrict__ gamma,
                                                     const float* __restrict__ mean,
@@ -372,6 +375,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_vec(const TY* __restrict__ dy, c
   // side's rate) instead of a workspace pass and a reduce kernel behind every LayerNorm backward
   for (int j = threadIdx.x; j < 2 * d; j += blockDim.x) {
     const float t = sm[0 * 2 * d + j] + sm[1 * 2 * d + j] + sm[2 * 2 * d + j] + sm[3 * 2 * d + j];
+    if constexpr (DET) { dgamma[(int64_t)blockIdx.x * 2 * d + j] = t; continue; }
     if (j < d) { if (dgamma) atomicAdd(dgamma + j, t); }
     else if (dbeta) atomicAdd(dbeta + j - d, t);
   }
@@ -435,8 +439,14 @@ static inline int ln_bwd_blocks(int64_t rows) {
 }
 // the vectorised backward adds its block sums to dgamma / dbeta with atomics and touches no workspace
 static inline bool ln_bwd_vectorised(const afm_ln_shape* s) { return (s->d % 8) == 0 && s->d <= 2048 && s->rows >= 64; }
+// deterministic mode (flags bit 1): block counts of the shape alone (AFM_LN_BWD_BLOCKS is not read)
+static inline int ln_bwd_det_blocks(const afm_ln_shape* s) {
+  if (ln_bwd_vectorised(s)) return (int)std::min<int64_t>((s->rows + 3) / 4, 256 * (s->d <= 512 ? 3 : s->d <= 1024 ? 2 : 1));
+  return (int)std::max<int64_t>(1, std::min<int64_t>((s->rows + 3) / 4, 768));
+}
 extern "C" int64_t afm_layernorm_bwd_ws_floats(const afm_ln_shape* s) {
   if (!s) return 0;
+  if (s->flags & 2) return s->rows > 0 ? (int64_t)ln_bwd_det_blocks(s) * 2 * s->d : 0;
   if (ln_bwd_vectorised(s)) return 0;
   return (int64_t)ln_bwd_blocks(s->rows) * 2 * s->d;
 }
@@ -540,10 +550,11 @@ extern "C" int afm_layernorm_bwd(const afm_ln_shape* s, const void* dy, const fl
   const DropDev dd = afm_make_drop(drop);
   if (!s || !dy || !x || !gamma || !mean || !rstd || !dx || s->rows < 0 || s->d <= 0)
     return AFM_ERR_ARG;
-  if (!partial && !ln_bwd_vectorised(s)) return AFM_ERR_ARG;      // (afm_layernorm_bwd_ws_floats says which shapes need it)
+  const bool det = (s->flags & 2) != 0;      // deterministic mode: block partials to `partial`, a fixed-order reduce (afm_det.h)
+  if (!partial && (det || !ln_bwd_vectorised(s))) return AFM_ERR_ARG;      // (afm_layernorm_bwd_ws_floats says which shapes need it)
   if (s->d > 64 * LN_MAXV) return AFM_ERR_UNSUPPORTED;
   if (s->rows == 0) return AFM_OK;
-  const int g = ln_bwd_blocks(s->rows);
+  const int g = det ? ln_bwd_det_blocks(s) : ln_bwd_blocks(s->rows);
   hipStream_t st = (hipStream_t)stream;
   const size_t shm = sizeof(float) * 8 * s->d;
   if (s->y_dtype < AFM_F32 || s->y_dtype > AFM_F16) return AFM_ERR_ARG;
@@ -551,16 +562,19 @@ extern "C" int afm_layernorm_bwd(const afm_ln_shape* s, const void* dy, const fl
   if (ln_bwd_vectorised(s)) {   // vectorised path (dy rows follow the embedder's placement, if any)
     // resident workgroups only, as in the forward: three per CU at d <= 512 (136 registers), two at d <= 1024 (229), one beyond (438)
     static const bool bwd_forced = getenv("AFM_LN_BWD_BLOCKS") != nullptr;
-    const int gv = bwd_forced ? g : (int)std::min<int64_t>((s->rows + 3) / 4, 256 * (s->d <= 512 ? 3 : s->d <= 1024 ? 2 : 1));
-#define LN_BV(TY, NC) AFM_LAUNCH((k_ln_bwd_vec<TY, NC>), dim3(gv), dim3(256), shm, st, (const TY*)dy, x, gamma, mean, rstd, dres, dx, \
-                                 dgamma, dbeta, s->rows, s->d, (TY*)dx_drop, dd, s->seg_len, s->out_seg_stride, s->out_off,   \
-                                 (s->seg_len == 0 && (s->rows & 63) == 0) ? s->row_live : nullptr, s->seg_len != 0 ? s->row_map : nullptr, (s->flags & 1) != 0)
+    const int gv = det ? g : bwd_forced ? g : (int)std::min<int64_t>((s->rows + 3) / 4, 256 * (s->d <= 512 ? 3 : s->d <= 1024 ? 2 : 1));
+#define LN_BV_(TY, NC, DET, DG) AFM_LAUNCH((k_ln_bwd_vec<TY, NC, DET>), dim3(gv), dim3(256), shm, st, (const TY*)dy, x, gamma, mean, rstd, \
+                                 dres, dx, DG, dbeta, s->rows, s->d, (TY*)dx_drop, dd, s->seg_len, s->out_seg_stride, s->out_off,   \
+                                 (s->seg_len == 0 && (s->rows & 63) == 0) ? s->row_live : nullptr, s->seg_len != 0 ? s->row_map : nullptr, \
+                                 (s->flags & 1) != 0)
+#define LN_BV(TY, NC) do { if (det) LN_BV_(TY, NC, true, partial); else LN_BV_(TY, NC, false, dgamma); } while (0)
 #define LN_BV2(TY) do { if (s->d <= 512) LN_BV(TY, 1); else if (s->d <= 1024) LN_BV(TY, 2); else LN_BV(TY, 4); } while (0)
     if (s->y_dtype == AFM_BF16) LN_BV2(bf16); else if (s->y_dtype == AFM_BF16X2) LN_BV2(x2); else if (s->y_dtype == AFM_F16) LN_BV2(f16); else LN_BV2(float);
 #undef LN_BV2
 #undef LN_BV
-    return AFM_OK;
-  }
+#undef LN_BV_
+    if (!det) return AFM_OK;
+  } else {
 #define LN_BWD(NV)                                                                                   \
   do {                                                                                               \
     AFM_DT_SWITCH(s->y_dtype, TY, AFM_LAUNCH((k_ln_bwd<TY, NV>), dim3(g), dim3(256), shm, st, (const TY*)dy, x,     \
@@ -572,6 +586,12 @@ extern "C" int afm_layernorm_bwd(const afm_ln_shape* s, const void* dy, const fl
   else if (nv <= 8) LN_BWD(8); else if (nv <= 12) LN_BWD(12); else if (nv <= 16) LN_BWD(16);
   else LN_BWD(32);
 #undef LN_BWD
+  }
+  if (det) {      // partial[block][0 .. d) -> dgamma, [d .. 2d) -> dbeta, blocks added in order
+    int r = dgamma ? afm_det_sum_launch(partial, g, 2 * (int64_t)s->d, 1, s->d, s->d, dgamma, s->d, 1, st) : AFM_OK;
+    if (r == AFM_OK && dbeta) r = afm_det_sum_launch(partial + s->d, g, 2 * (int64_t)s->d, 1, s->d, s->d, dbeta, s->d, 1, st);
+    return r;
+  }
   AFM_LAUNCH(k_ln_bwd_reduce, dim3((2 * s->d + 63) / 64, g >= 64 ? 16 : 1), dim3(256), 0, st, partial, dgamma,
                      dbeta, g, s->d);
   return AFM_OK;

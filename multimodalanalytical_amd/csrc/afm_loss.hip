@@ -2,7 +2,11 @@
 // One 64-lane wave per row of logits; V is the SMILES vocabulary (tens to a few hundred), so a
 // row is one or two loads per lane and the kernel is a single pass over the logits.
 #include "afm_common.h"
+#include "afm_det.h"
 
+// DET (afm_ce_fwd_det): `stats` is the workspace, block b stores its loss and count to stats[2b], stats[2b + 1]; DET = false is the
+// default kernel, unchanged.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_ce_fwd(const float* __restrict__ logits,
                                                 const int64_t* __restrict__ labels, int64_t rows,
                                                 int V, int ld, float* __restrict__ row_lse,
@@ -42,6 +46,11 @@ __global__ __launch_bounds__(256) void k_ce_fwd(const float* __restrict__ logits
   __syncthreads();
   if (threadIdx.x == 0 && stats) {
     const float c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if constexpr (DET) {
+      stats[2 * blockIdx.x] = s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3];
+      stats[2 * blockIdx.x + 1] = c;
+      return;
+    }
     if (c > 0.f) {
       atomicAdd(stats + 0, s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3]);
       atomicAdd(stats + 1, c);
@@ -53,9 +62,22 @@ extern "C" int afm_ce_fwd(const float* logits, const int64_t* labels, int64_t ro
                           int32_t ld, float* row_lse, int64_t* argmax, float* stats, void* stream) {
   if (!logits || rows < 0 || V <= 0 || ld < V) return AFM_ERR_ARG;
   if (rows == 0) return AFM_OK;
-  AFM_LAUNCH(k_ce_fwd, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+  AFM_LAUNCH(k_ce_fwd<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                      logits, labels, rows, V, ld, row_lse, argmax, stats);
   return AFM_OK;
+}
+
+// Deterministic form: the per-block (4 rows) loss sums and counts go to `ws`, one workgroup adds them in a fixed order into stats.
+extern "C" int64_t afm_ce_fwd_det_ws_floats(int64_t rows) { return rows < 0 ? -1 : 2 * ((rows + 3) / 4); }
+extern "C" int afm_ce_fwd_det(const float* logits, const int64_t* labels, int64_t rows, int32_t V, int32_t ld, float* row_lse,
+                              int64_t* argmax, float* stats, float* ws, int64_t ws_floats, void* stream) {
+  if (!logits || rows < 0 || V <= 0 || ld < V) return AFM_ERR_ARG;
+  if (stats && rows > 0 && (!ws || ws_floats < afm_ce_fwd_det_ws_floats(rows))) return AFM_ERR_ARG;
+  if (rows == 0) return AFM_OK;
+  const int blocks = (int)((rows + 3) / 4);
+  hipStream_t st = (hipStream_t)stream;
+  AFM_LAUNCH(k_ce_fwd<true>, dim3((unsigned)blocks), dim3(256), 0, st, logits, labels, rows, V, ld, row_lse, argmax, stats ? ws : nullptr);
+  return stats ? afm_det_total_launch(ws, blocks, 2, stats, st) : AFM_OK;
 }
 
 template <typename T>

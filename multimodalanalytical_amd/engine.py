@@ -50,7 +50,7 @@ class Seq2SeqEngine:
 
     def __init__(self, cfg: Dict[str, Any], data_config: Dict[str, Any], target_modality: str,
                  vocab_out: int, device="cuda:0", compute_dtype=torch.bfloat16, seed: int = 3247,
-                 algo: int = ALGO_AUTO, side_wgrad: bool = False, backward_dtype=None):
+                 algo: int = ALGO_AUTO, side_wgrad: bool = False, backward_dtype=None, deterministic: Optional[bool] = None):
         self.cfg = dict(cfg)
         self.cfg.setdefault("multimodal_norm", True)
         self.cfg.setdefault("gated_linear", False)
@@ -120,6 +120,11 @@ class Seq2SeqEngine:
         self.wgrad_layers = max(1, int(os.environ.get("AFM_WGRAD_LAYERS", "1")))
         self._wg_layers_pending = 0
         self.row_skip = os.environ.get("AFM_ROW_SKIP", "1") != "0"          # (0: the backward computes padded rows like any other)
+        # deterministic mode (AFM_DETERMINISTIC=1, or deterministic=True; Lightning's Trainer(deterministic=True)): every reduction over
+        # tokens of a step takes its atomic-free form (ops.deterministic: fixed-order workspace sums), so one GPU gives the same bits
+        # in every run.  Off: the default kernels, unchanged.  The workspaces persist, one per stream (the side wgrad stream has its own).
+        self.deterministic = (os.environ.get("AFM_DETERMINISTIC", "0") == "1") if deterministic is None else bool(deterministic)
+        self._det_ws = ops.DetWorkspace(self.dev) if (self.deterministic and self.dev.type == "cuda") else None
         # layer options of configs/model/*.yaml beside the defaults: the reference's `post_layer_normalisation` IS torch's norm_first
         # (custom_modeling.py:129,176: True = pre-LN, the shipped setting); `activation_function` goes to the torch layers as is
         self.pre_ln = bool(cfg.get("post_layer_normalisation", True))
@@ -1271,8 +1276,13 @@ class Seq2SeqEngine:
         ops.masked_mean_bwd(dpooled, mem_pad, B, S, dmem, accumulate=False)
         return stats[0], dmem
 
-    def forward(self, enc_inputs, attention_mask, dec_ids, dec_attention_mask=None, labels=None,
-                backward: bool = False, loss_scale: float = 1.0, memory=None, encoder_align_target=None):
+    def forward(self, *args, **kwargs):
+        """See _forward.  In deterministic mode every reduction of the call runs in its atomic-free form."""
+        with ops.deterministic(self._det_ws):
+            return self._forward(*args, **kwargs)
+
+    def _forward(self, enc_inputs, attention_mask, dec_ids, dec_attention_mask=None, labels=None,
+                 backward: bool = False, loss_scale: float = 1.0, memory=None, encoder_align_target=None):
         """One pass.  With `backward` the parameter gradients are ACCUMULATED into the flat
         gradient buffer (scaled by loss_scale, e.g. 1/acc_batches).  Returns a dict with fp32
         `logits` (B,T,V), `loss` (0-dim device tensor, mean over labels != -100), `argmax`

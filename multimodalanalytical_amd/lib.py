@@ -139,6 +139,18 @@ _SIGS = {
     "afm_place_rows": (C.c_int, [_P, _P, _P, _I64, _I32, _I64, _I64, _I64, _I32, _P]),
     "afm_compact_plan": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "afm_permute_rows": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    # deterministic mode (include/afm_hip.h): atomic-free reductions with caller workspaces
+    "afm_gemm_group_det_ws_floats": (C.c_int64, [_P, C.c_int32]),
+    "afm_gemm_group_det": (C.c_int, [_P, C.c_int32, _P, _I64, _P]),
+    "afm_colsum_det_ws_floats": (C.c_int64, [_I64, _I32]),
+    "afm_colsum_det": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "afm_scatter_add_rows_det": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P]),
+    "afm_ce_fwd_det_ws_floats": (C.c_int64, [_I64]),
+    "afm_ce_fwd_det": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "afm_masked_mean_fwd_det_ws_floats": (C.c_int64, [_I32, _I32, _I32]),
+    "afm_masked_mean_fwd_det": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P, _P, _I64, _P]),
+    "afm_align_loss_det_ws_floats": (C.c_int64, [_I32, _I32]),
+    "afm_align_loss_det": (C.c_int, [_P, _P, _I32, _I32, _I32, _F, _P, _P, _P, _P, _I64, _P]),
     "afm_comm_unique_id": (C.c_int, [_P]),
     "afm_comm_create": (C.c_int, [C.POINTER(_P), _P, _I32, _I32]),
     "afm_allreduce_bucket": (C.c_int, [_P, _P, _I64, _P]),

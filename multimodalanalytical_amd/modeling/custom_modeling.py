@@ -84,7 +84,7 @@ class CustomModel:
 
     def __init__(self, target_modality, target_tokenizer, config: CustomConfig,
                  multimodal_embedding_layer: MultimodalEmbedding, device="cuda:0",
-                 compute_dtype=torch.bfloat16, seed: int = 3247, backward_dtype=None):
+                 compute_dtype=torch.bfloat16, seed: int = 3247, backward_dtype=None, deterministic=None):
         self.config = config
         self.target_modality = target_modality
         self.decoder_vocab_size = target_tokenizer.vocab_size
@@ -93,7 +93,7 @@ class CustomModel:
         cfg["multimodal_norm"] = multimodal_embedding_layer.embedding_norm
         self.engine = Seq2SeqEngine(cfg, multimodal_embedding_layer.data_config, target_modality,
                                     self.decoder_vocab_size, device=device, compute_dtype=compute_dtype, seed=seed,
-                                    backward_dtype=backward_dtype)
+                                    backward_dtype=backward_dtype, deterministic=deterministic)
         multimodal_embedding_layer.engine = self.engine
         self.encoder = _EncoderHandle(self)
         self._grad_enabled, self._loss_scale = False, 1.0

@@ -54,6 +54,55 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+# ---------------------------------------------------------------------------------------------- deterministic mode
+class DetWorkspace:
+    """Persistent fp32 workspaces of the deterministic (*_det) exports, one per HIP stream (two streams never share a slab region).
+    A buffer grows to the largest request seen on its stream and is then reused: after the first step of a shape nothing is
+    allocated."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._bufs = {}
+
+    def get(self, floats: int) -> torch.Tensor:
+        floats = max(int(floats), 4)
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        b = self._bufs.get(key)
+        if b is None or b.numel() < floats:
+            b = torch.empty(floats, dtype=torch.float32, device=self.device)
+            self._bufs[key] = b
+        return b
+
+
+_DET: Optional[DetWorkspace] = None   # set by `deterministic(ws)`: every reduction below takes its atomic-free form
+
+
+class deterministic:
+    """`with ops.deterministic(ws):` routes every call below that reduces over tokens (weight gradients, column sums, LayerNorm
+    dgamma / dbeta, the embedding scatter-add, the loss sums, the alignment pooling) to its deterministic export, using `ws`
+    (a DetWorkspace; None: the default kernels).  Nests; restores the previous setting on exit."""
+
+    def __init__(self, ws: Optional[DetWorkspace]):
+        self.ws, self.prev = ws, None
+
+    def __enter__(self):
+        global _DET
+        self.prev, _DET = _DET, self.ws
+        return self.ws
+
+    def __exit__(self, *exc):
+        global _DET
+        _DET = self.prev
+        return False
+
+
+def _det_ws(ws, device) -> Optional[DetWorkspace]:
+    """The workspace a *_det wrapper uses: the one given, else the active one, else a fresh one."""
+    if ws is not None:
+        return ws
+    return _DET if _DET is not None else DetWorkspace(device)
+
+
 def _ld(t) -> int:
     """Row stride (elements) of a 2-D view whose last dim is contiguous."""
     if isinstance(t, X2):
@@ -191,6 +240,8 @@ def gemm_desc(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, *, trans_a=Fals
     d.reserved = int(variant)
     d.glu_rows = int(glu_rows)
     d.reserved2 = 1 if sg_hi_only else 0
+    if _DET is not None:
+        d.reserved2 |= 16       # deterministic result: no split-K atomics (the wgrad form goes to afm_gemm_group_det)
     d.drop = dropout
     nofill = (isinstance(rows_unread, RowFlags) and rows_unread.nofill) or (isinstance(k_live, RowFlags) and k_live.nofill and not trans_a)
     d._hint_tag = k_live.tag if isinstance(k_live, RowFlags) else (rows_unread.tag if isinstance(rows_unread, RowFlags) else "")
@@ -218,6 +269,9 @@ def gemm(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, **kw) -> torch.Tenso
     a_colsum (trans_a only): a_colsum[m] += sum_k a[k, m], the bias gradient of the wgrad form.
     Gated-FFN forms (act 6 / 7 / 8, include/afm_hip.h): c is (M, N/2) resp. (M, 2N); glu_rows = f."""
     d = gemm_desc(a, b, c, **kw)
+    if _DET is not None and d.transA and not d.transB:
+        gemm_group_det([d])
+        return c
     L.check(L.load().afm_gemm(C.byref(d), _stream()), "afm_gemm")
     _log_algo()
     _note_hint([d._hint_tag] if d.k_live else [], bool(d.reserved2 & 8) and not (d.reserved2 & 2), f"afm_gemm M={d.M} N={d.N} K={d.K} ta={d.transA} act={d.act}")
@@ -232,11 +286,34 @@ def gemm_group(descs) -> None:
     """afm_gemm_group: the GEMMs of `descs` (gemm_desc objects), weight-gradient problems fused into shared launches."""
     if not descs:
         return
+    if _DET is not None:
+        gemm_group_det(descs)
+        return
     arr = (GemmDesc * len(descs))(*descs)
     L.check(L.load().afm_gemm_group(C.cast(arr, C.c_void_p), len(descs), _stream()), "afm_gemm_group")
     _log_algo()
     _note_hint([d._hint_tag for d in descs if d.k_live], False, "afm_gemm_group " + " ".join(f"{d.M}x{d.N}x{d.K}" for d in descs))
 
+
+
+def gemm_group_det_ws(descs) -> int:
+    """Workspace floats afm_gemm_group_det needs for these weight-gradient descriptors (host-only, shapes only; -1: not the form)."""
+    arr = (GemmDesc * len(descs))(*descs)
+    return int(L.load().afm_gemm_group_det_ws_floats(C.cast(arr, C.c_void_p), len(descs)))
+
+
+def gemm_group_det(descs, ws: Optional[DetWorkspace] = None) -> None:
+    """afm_gemm_group_det: the weight gradients of `descs` without atomics (fixed split-K slabs reduced in order)."""
+    if not descs:
+        return
+    arr = (GemmDesc * len(descs))(*descs)
+    need = int(L.load().afm_gemm_group_det_ws_floats(C.cast(arr, C.c_void_p), len(descs)))
+    if need < 0:
+        raise L.AfmError("afm_gemm_group_det: not a weight-gradient problem: " + " ".join(f"{d.M}x{d.N}x{d.K}" for d in descs))
+    buf = _det_ws(ws, torch.device("cuda", torch.cuda.current_device())).get(need)
+    L.check(L.load().afm_gemm_group_det(C.cast(arr, C.c_void_p), len(descs), _ptr(buf), buf.numel(), _stream()), "afm_gemm_group_det")
+    _log_algo()
+    _note_hint([d._hint_tag for d in descs if d.k_live], False, "afm_gemm_group_det " + " ".join(f"{d.M}x{d.N}x{d.K}" for d in descs))
 
 def gather_rows(ids, table, out, scale=None):
     n = ids.numel()
@@ -251,8 +328,30 @@ def scatter_add_rows(ids, dout, dtable, scale=None, padding_idx=-1):
     n = ids.numel()
     V, d = dtable.shape
     assert ids.dtype == torch.int64 and ids.is_contiguous() and dout.is_contiguous()
+    if _DET is not None:
+        return scatter_add_rows_det(ids, dout, dtable, scale, padding_idx)
     L.check(L.load().afm_scatter_add_rows(_ptr(ids), _ptr(scale), _ptr(dout), _ptr(dtable), n, d, V,
                                           int(padding_idx), _stream()), "afm_scatter_add_rows")
+
+
+def scatter_add_rows_det(ids, dout, dtable, scale=None, padding_idx=-1):
+    """afm_scatter_add_rows_det: each table row gets its rows of dout (x scale) added one after another in ascending row order.
+    The row order by id comes from a stable device sort (torch); the summation is the library's."""
+    n = ids.numel()
+    V, d = dtable.shape
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and dout.is_contiguous()
+    if n == 0:
+        return
+    flat = ids.view(-1)
+    key = torch.where(flat == int(padding_idx), torch.full_like(flat, V), flat.clamp(0, V - 1))      # padding rows last (skipped)
+    order = torch.argsort(key, stable=True)
+    # seg_end[i] = the first sorted position after i where the key changes (n: none), a suffix minimum: no host synchronisation
+    skey = key[order]
+    pos = torch.arange(n, device=ids.device)
+    starts = torch.where(torch.cat([skey.new_ones(1, dtype=torch.bool), skey[1:] != skey[:-1]]), pos, n)
+    seg_end = torch.cat([starts[1:], starts.new_full((1,), n)]).flip(0).cummin(0).values.flip(0).contiguous()
+    L.check(L.load().afm_scatter_add_rows_det(_ptr(ids), _ptr(order), _ptr(seg_end), _ptr(scale), _ptr(dout), _ptr(dtable), n, d, V,
+                                              int(padding_idx), _stream()), "afm_scatter_add_rows_det")
 
 
 def ln_shape(rows, d, y_dtype, seg_len=0, out_seg_stride=0, out_off=0, eps=1e-5) -> LnShape:
@@ -287,8 +386,10 @@ def layernorm_fwd(x, gamma, beta, y, mean=None, rstd=None, pos=None, seg_len=0, 
     return y
 
 
-def layernorm_bwd_ws(rows, d) -> int:
+def layernorm_bwd_ws(rows, d, det: bool = False) -> int:
     s = ln_shape(rows, d, torch.float32)
+    if det:
+        s.flags |= 2
     return int(L.load().afm_layernorm_bwd_ws_floats(C.byref(s)))
 
 
@@ -308,7 +409,10 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, dres=None, se
         assert row_live.dtype == torch.uint8 and row_live.is_contiguous() and rows % 64 == 0 and row_live.numel() == rows // 64
         assert seg_len == 0
         s.row_live = _ptr(row_live)
-    assert ws.numel() >= layernorm_bwd_ws(rows, d)
+    if _DET is not None:      # deterministic: dgamma / dbeta through block partials and a fixed-order reduce (flags bit 1)
+        s.flags |= 2
+        ws = _DET.get(layernorm_bwd_ws(rows, d, det=True))
+    assert ws.numel() >= layernorm_bwd_ws(rows, d, det=_DET is not None)
     if dx_drop is not None:
         assert dx_drop.dtype == dy.dtype and dx_drop.shape == x.shape and is_contig(dx_drop) and is_contig(dy)
     L.check(L.load().afm_layernorm_bwd(C.byref(s), _ptr(dy), _ptr(x), _ptr(gamma), _ptr(mean), _ptr(rstd),
@@ -468,8 +572,19 @@ def dropout_cast(x, y, dropout: Dropout = NO_DROP):
 def colsum(x, out, accumulate=True):
     rows, n = x.shape
     assert out.dtype == torch.float32 and out.numel() == n
+    if _DET is not None:
+        return colsum_det(x, out, accumulate)
     L.check(L.load().afm_colsum(_ptr(x), _ptr(out), rows, n, _ld(x), _dt(x), int(accumulate), _stream()),
             "afm_colsum")
+    return out
+
+
+def colsum_det(x, out, accumulate=True, ws: Optional[DetWorkspace] = None):
+    rows, n = x.shape
+    assert out.dtype == torch.float32 and out.numel() == n
+    buf = _det_ws(ws, out.device).get(L.load().afm_colsum_det_ws_floats(rows, n))
+    L.check(L.load().afm_colsum_det(_ptr(x), _ptr(out), rows, n, _ld(x), _dt(x), int(accumulate), _ptr(buf), buf.numel(), _stream()),
+            "afm_colsum_det")
     return out
 
 
@@ -557,6 +672,11 @@ def masked_mean_fwd(x, key_pad, B, S, out):
     """out (B, d) fp32 = mean over the kept rows of x (B*S, d); key_pad (B, S) uint8, 1 = pad."""
     d = x.shape[-1]
     assert is_contig(x) and key_pad.dtype == torch.uint8 and out.dtype == torch.float32
+    if _DET is not None:
+        buf = _DET.get(L.load().afm_masked_mean_fwd_det_ws_floats(B, S, d))
+        L.check(L.load().afm_masked_mean_fwd_det(_ptr(x), _dt(x), _ptr(key_pad), B, S, d, _ptr(out), _ptr(buf), buf.numel(), _stream()),
+                "afm_masked_mean_fwd_det")
+        return
     L.check(L.load().afm_masked_mean_fwd(_ptr(x), _dt(x), _ptr(key_pad), B, S, d, _ptr(out), _stream()), "afm_masked_mean_fwd")
 
 
@@ -569,6 +689,11 @@ def masked_mean_bwd(dy, key_pad, B, S, dx, accumulate=False):
 def align_loss(z, target, kind: str, grad_scale, stats, dz=None, scale_dev=None):
     B, n = z.shape
     assert z.dtype == torch.float32 and target.dtype == torch.float32 and z.is_contiguous() and target.is_contiguous()
+    if _DET is not None:
+        buf = _DET.get(L.load().afm_align_loss_det_ws_floats(B, n))
+        L.check(L.load().afm_align_loss_det(_ptr(z), _ptr(target), ALIGN_KINDS[kind], B, n, float(grad_scale), _ptr(scale_dev),
+                                            _ptr(stats), _ptr(dz), _ptr(buf), buf.numel(), _stream()), "afm_align_loss_det")
+        return
     L.check(L.load().afm_align_loss(_ptr(z), _ptr(target), ALIGN_KINDS[kind], B, n, float(grad_scale), _ptr(scale_dev),
                                     _ptr(stats), _ptr(dz), _stream()), "afm_align_loss")
 
@@ -639,6 +764,11 @@ def cache_reorder(src, dst, beam_idx, rows: int, block_bytes: int, used_bytes: i
 def ce_fwd(logits, labels, row_lse, argmax, stats):
     rows, V = logits.shape
     assert logits.dtype == torch.float32 and labels.dtype == torch.int64
+    if _DET is not None:
+        buf = _DET.get(L.load().afm_ce_fwd_det_ws_floats(rows))
+        L.check(L.load().afm_ce_fwd_det(_ptr(logits), _ptr(labels), rows, V, _ld(logits), _ptr(row_lse), _ptr(argmax),
+                                        _ptr(stats), _ptr(buf), buf.numel(), _stream()), "afm_ce_fwd_det")
+        return
     L.check(L.load().afm_ce_fwd(_ptr(logits), _ptr(labels), rows, V, _ld(logits), _ptr(row_lse), _ptr(argmax),
                                 _ptr(stats), _stream()), "afm_ce_fwd")
 
