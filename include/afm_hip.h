@@ -449,6 +449,28 @@ int afm_mix_spectra(const float* table, int64_t N, int32_t L, const int64_t* idx
                     const double* ratio, int32_t normalize, int32_t out_len, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training-set augmentation (data/augmentations.py:12-39, applied at data/datasets.py:377-378; the `augment`
+ * config group).  Output row r (0 <= r < M) is op op[r] applied to table[src[r]] (src clamped into [0, N)):
+ *   AFM_AUG_COPY    the row unchanged;
+ *   AFM_AUG_GAUSS   (a = radius R, b = offset into `weights`): scipy.ndimage.gaussian_filter1d(row, sigma), mode "reflect"
+ *                   (period 2L, so R > L is legal): x[i] w0 + sum_{q = R .. 1} (x[i-q] + x[i+q]) w_q in fp64, in that order,
+ *                   with w_0 .. w_R = weights[b .. b+R] = the normalised half kernel SciPy builds (_gaussian_kernel1d: computed
+ *                   on the host with numpy, exp is never evaluated here);
+ *   AFM_AUG_HSHIFT  (a = n, b = i < n): horizontal_shift_augment output i: row[i::n] on the knots np.linspace(0, L, L / n)
+ *                   resampled at 0..L-1 by np.interp (what interp1d calls for 1-D float64 data) in fp64.  L % n == 0 is
+ *                   AFM_ERR_ARG: the reference's slice then has one point fewer than the knots and interp1d raises.
+ * Every value is rounded once to fp32.  op_desc_host: n_ops x {kind, a, b} int32 in HOST memory (validated here, at most
+ * AFM_AUG_MAX_OPS); op (M) int32 indexes it on the device, an index outside [0, n_ops) yields a NaN row.  table (N x L) fp32,
+ * out (M x L) fp32, weights (n_weights) fp64 (may be NULL without a gauss op).  L > 4096 or R > 2048: AFM_ERR_UNSUPPORTED.
+ * Pinned: tests/golden/augment.npz holds the reference's own augment() on seeded tables (tools/make_augment_goldens.py);
+ * this kernel and the numpy restatement tests/augment_numpy.py reproduce np.float32 of it bit for bit.
+ * ---------------------------------------------------------------------------------------- */
+enum { AFM_AUG_COPY = 0, AFM_AUG_GAUSS = 1, AFM_AUG_HSHIFT = 2, AFM_AUG_MAX_OPS = 32 };
+int afm_spectra_augment(const float* table, int64_t N, int32_t L, const int64_t* src, const int32_t* op, int64_t M,
+                        const int32_t* op_desc_host, int32_t n_ops, const double* weights, int64_t n_weights,
+                        float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Input path: PatchPreprocessor.__call__ (data/preprocessing/patches.py:54-107)
  * on the device.  spectra (B x L) fp32 rows, present[b] = 0 marks the reference's `None` spectrum
  * (zeros BEFORE standardisation, patches.py:63-67).  Per row, in the reference's order:

@@ -17,6 +17,9 @@ therefore points at PRE-TOKENISED shards, `{train,val,test}.pt`, each `{"meta": 
 "data": {modality: {"input_ids", "attention_mask"} | {"spectra"[, "present"]}}}` (text-like modalities as padded id
 matrices, patch modalities as raw spectra; `multimodalanalytical_amd.synth.write_shards` writes synthetic ones), or
 `data_path=synthetic:<n_train>` to generate them on the fly from the composed data config.
+The `augment` group (`augment=ir/smooth`, `ir/horizontal`, `ir/pseudo`) expands the train split on the device before anything
+counts or samples it (`augment_train`, multimodalanalytical_amd/augment.py); `+augment.on_the_fly=true` makes the expanded rows
+per micro-batch instead.
 Like the reference the run is wrapped in one try/except that logs and returns 0 unless `strict=1` is passed.
 """
 from __future__ import annotations
@@ -116,7 +119,8 @@ class ShardLoader:
                  drop_last: bool = True):
         self.shard, self.collator, self.bs, self.dev = shard, collator, int(batch_size), device
         self.rank, self.world, self.shuffle, self.drop_last = rank, world, shuffle, drop_last
-        self.n = shard_len(shard)
+        self.aug = shard.get("augment")      # +augment.on_the_fly=true: an augment.OnTheFly, the rows of the expanded set made per batch
+        self.n = self.aug.rows if self.aug is not None else shard_len(shard)
         self.dev_data = {m: {k: v.to(device) for k, v in d.items()} for m, d in shard["data"].items()}   # resident in HBM
         # AFM_SORT_BATCH=1 / 2 (training shuffles only; A / B probes, OFF by default): the samples of a micro-batch in order of decreasing
         # encoder length (1), or that order dealt in a snake over the batch's eight contiguous eighths (2).  Which samples share a batch
@@ -129,6 +133,8 @@ class ShardLoader:
             masks = [d["attention_mask"].sum(1) for m, d in self.dev_data.items() if m in inputs and "attention_mask" in d]
             if masks:
                 self.sort_len = torch.stack(masks, 0).sum(0)
+                if self.aug is not None:
+                    self.sort_len = self.sort_len.index_select(0, self.aug.src)
 
     def __len__(self):
         per_rank = self.n // self.world
@@ -148,7 +154,12 @@ class ShardLoader:
                     n8 = idx.numel() // 8
                     j = torch.arange(8, device=idx.device)[:, None]; r = torch.arange(n8, device=idx.device)[None, :]
                     idx = idx[(8 * r + torch.where(r % 2 == 0, j, 7 - j)).reshape(-1)]
-            yield self.collator({m: {k: v.index_select(0, idx) for k, v in d.items()} for m, d in self.dev_data.items()})
+            yield self.collator(self.rows(idx))
+
+    def rows(self, idx):
+        if self.aug is not None:
+            return self.aug.gather(self.dev_data, idx)
+        return {m: {k: v.index_select(0, idx) for k, v in d.items()} for m, d in self.dev_data.items()}
 
 
 class MixtureLoader:
@@ -253,7 +264,7 @@ def build_preprocessors(train_shard, data_config, device, mixture_sample=None):
                                    interpolation=bool(a.get("interpolation", False)), overlap=int(a.get("overlap", 1)),
                                    derivative=bool(a.get("derivative", False)), device=device)
             # data_utils.py:49-59: statistics from (up to) the first 10 000 records -- of the mixture stream when there is one
-            # (`data_set.take(num_samples)`), else a sample of the training shard
+            # (`data_set.take(num_samples)`) or of the expanded set made on the fly, else a sample of the training shard
             if mixture_sample is not None and m in mixture_sample:
                 sample = mixture_sample[m]
             elif m in train_shard["data"]:
@@ -266,6 +277,34 @@ def build_preprocessors(train_shard, data_config, device, mixture_sample=None):
     return pre
 
 
+def augment_train(cfg: Dict[str, Any], train, device: str, mixture=None):
+    """`augment(dataset_dict["train"], config["augment"])` (datasets.py:377-378, augmentations.py:57-107) on the device:
+    (train shard, None) with the expanded rows materialised, or, with `+augment.on_the_fly=true`, (the 1x shard carrying an
+    `augment.OnTheFly` under "augment", the first min(10 000, M) expanded spectra for the PatchPreprocessor statistics).
+    No augment group / no_augment: the shard unchanged."""
+    from .. import augment as A
+    acfg = cfg.get("augment")
+    if not isinstance(acfg, dict):
+        return train, None
+    if acfg.get("on_the_fly") and isinstance(mixture, dict):
+        raise NotImplementedError("+augment.on_the_fly=true with a `mixture` group: the mixture generator draws from the "
+                                  "materialised expanded set; drop on_the_fly to augment before mixing")
+    plan = A.plan_augmentation(acfg, cfg["data"], train)      # every refusal before augment_data_path is read
+    extra = None
+    if acfg.get("augment_data_path"):
+        extra = A.load_extra(acfg["augment_data_path"], train["meta"])
+        plan = A.plan_augmentation(acfg, cfg["data"], train, n_extra=A.shard_rows(extra))
+    if plan is None:
+        return train, None
+    if not plan.on_the_fly:
+        return A.materialise(train, plan, device, extra), None
+    fly = A.OnTheFly(plan, device)
+    data = {m: {k: v.to(device) for k, v in d.items()} for m, d in A.base_data(train, extra).items()}
+    head = torch.arange(min(10000, plan.rows), device=device)
+    sample = {m: d["spectra"] for m, d in fly.gather({m: d for m, d in data.items() if "spectra" in d}, head).items()}
+    return {"meta": train["meta"], "data": data, "augment": fly}, sample
+
+
 def setup_data(cfg: Dict[str, Any], device: str, world: int = 1):
     """Shards, run plan, collator and the mixture group of a composed config (the reference's build_dataset_multimodal +
     load_preprocessors + MultiModalDataModule, cli/training.py:80-131)."""
@@ -273,7 +312,9 @@ def setup_data(cfg: Dict[str, Any], device: str, world: int = 1):
     shards = load_shards(cfg["data_path"], cfg, device)
     meta = shards["train"]["meta"]
     mixture = cfg.get("mixture")            # cli/training.py:86-94 hands it to the dataset builder (datasets.py:395-412)
-    n_train = shard_len(shards["train"])
+    # the `augment` group expands the train split before anything counts or samples it (datasets.py:377-378 runs first)
+    shards["train"], aug_sample = augment_train(cfg, shards["train"], device, mixture)
+    n_train = shards["train"]["augment"].rows if "augment" in shards["train"] else shard_len(shards["train"])
     if isinstance(mixture, dict):
         n_train = sum(int(c.get("train_max_n_samples", 0)) for c in mixture.values())      # the iterable's nominal length
     plan = build_plan(cfg, meta, n_train, world, bool(cfg["trainer"].get("legacy_step_count", False)))
@@ -289,7 +330,7 @@ def setup_data(cfg: Dict[str, Any], device: str, world: int = 1):
         if got:
             mix_sample = {probe.spec: torch.cat(got)[:10000]}
         del probe
-    pre = build_preprocessors(shards["train"], dc, device, mix_sample)
+    pre = build_preprocessors(shards["train"], dc, device, mix_sample if mix_sample is not None else aug_sample)
     return shards, plan, DeviceCollator(dc, pre, tm), (mixture if isinstance(mixture, dict) else None)
 
 

@@ -711,6 +711,26 @@ def mix_spectra(table, idx, ratio, normalize=False, out_len=1800):
     return out
 
 
+AUG_COPY, AUG_GAUSS, AUG_HSHIFT = 0, 1, 2      # afm_spectra_augment op kinds (include/afm_hip.h)
+
+
+def spectra_augment(table, src, op, op_desc, weights=None):
+    """Augmented rows on the device: row r = op_desc[op[r]] applied to table[src[r]].  table (N, L) fp32, src (M,) int64 and
+    op (M,) int32 on the device; op_desc (K, 3) int32 {kind, a, b} on the HOST (AUG_COPY | AUG_GAUSS radius, weight offset |
+    AUG_HSHIFT n, i); weights fp64 (the Gaussian half kernels), on the device or moved there.  Returns (M, L) fp32."""
+    N, Ln = table.shape
+    assert table.dtype == torch.float32 and table.is_contiguous()
+    assert src.dtype == torch.int64 and src.is_contiguous() and op.dtype == torch.int32 and op.is_contiguous()
+    M = src.numel()
+    assert op.numel() == M
+    desc = torch.as_tensor(op_desc, dtype=torch.int32).cpu().contiguous().reshape(-1, 3)
+    w = None if weights is None else torch.as_tensor(weights, dtype=torch.float64, device=table.device).contiguous()
+    out = torch.empty(M, Ln, dtype=torch.float32, device=table.device)
+    L.check(L.load().afm_spectra_augment(_ptr(table), N, Ln, _ptr(src), _ptr(op), M, desc.data_ptr(), desc.shape[0], _ptr(w),
+                                         0 if w is None else w.numel(), _ptr(out), _stream()), "afm_spectra_augment")
+    return out
+
+
 def patch_preprocess(spectra, present, mean, std, patch_size, masking=False, interpolation=False, overlap=1,
                      derivative=False, seq_first=False):
     """PatchPreprocessor.__call__ on the device: spectra (B, L) fp32, present (B,) bool/uint8 or None.
